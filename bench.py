@@ -471,12 +471,39 @@ def dist_selftest(args):
         print(json.dumps({"selftest": "dist", "n_gpus": world, "rccl": probe}))
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(outdir, out, model):
+    """--dump-outputs: what the timed step handed its caller (train_step's dict) and the parameters it left behind, as
+    <outdir>/<name>.npy (float32; python scalars float64).  Over DUMP_LIMIT_BYTES in all, each array above its share keeps a
+    fixed, seeded sample of its flattened elements (<name>.sample.npy; the same indices on every run)."""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().float().cpu().numpy()
+        elif isinstance(v, (int, float)):
+            arrays[k] = np.asarray(v, dtype=np.float64)
+    for k, v in model.named_parameters():
+        arrays["param." + k] = v.detach().float().cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES - (1 << 20)      # (room for the .npy headers)
+    share = budget // max(len(arrays), 1)
+    for k, a in sorted(arrays.items()):
+        name = k
+        if sum(b.nbytes for b in arrays.values()) > budget and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(1238).choice(a.size, share // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], k + ".sample"
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def train_leg(args, dev, rank, world, dtype, hidden, enc_layers, batch, seq_len, steps, warmup, min_sustain_s=0.0, graph=False, z_dim=None,
-              cell=None, dec_layers=1, opts=None):
+              cell=None, dec_layers=1, opts=None, dump_dir=None):
     """One timed WAE-training leg: builds the model at the given dimensions, W untimed steps, EXACTLY `steps` timed steps
     bracketed by barrier + synchronize, max over ranks.  Returns the numbers of the leg (rank 0 builds the roofline rows).
     min_sustain_s > 0: afterwards the same step keeps running until that much wall time has passed (`sustained`): the timed
-    region of the default K=20 is 0.14 s, too short for an SMI sampler to see the GPU busy."""
+    region of the default K=20 is 0.14 s, too short for an SMI sampler to see the GPU busy.
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs) before anything else runs a step."""
     import cfg
     import losses
     from cpg import dist as cdist
@@ -541,6 +568,8 @@ def train_leg(args, dev, rank, world, dtype, hidden, enc_layers, batch, seq_len,
     dt = float(tmax.item())
     loss_val = float(out["L_vae"].item())
     assert np.isfinite(loss_val), "non-finite loss in the timed region"
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, out, model)
     ops.check_persistent()
     ms = dt / steps * 1e3
     res = {"value": round(B * world * steps / dt, 1), "ms_per_step": round(ms, 3), "steps": steps, "warmup": warmup,
@@ -658,6 +687,8 @@ def main():
     ap.add_argument("--class-proposals", type=int, default=1000000, help="z proposals of the CLaSS leg (BASELINE.json configs[3]: 1 M in total, sharded over the ranks)")
     ap.add_argument("--all-legs", action="store_true", help="N > 1: also run the config-C leg (skipped by default to bound the wall time)")
     ap.add_argument("--dist-selftest", action="store_true", help="CPU-only check of the N>1 launcher + collectives (gloo); no GPU work")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline leg's last timed step (train_step's outputs, the updated parameters) to DIR/<name>.npy")
     args = ap.parse_args()
 
     maybe_self_spawn(args)
@@ -686,7 +717,7 @@ def main():
     t_start = time.perf_counter()
     note("headline leg")
     head = train_leg(args, dev, rank, world, args.dtype, Hh, args.enc_layers, B, T, args.steps, args.warmup,
-                     0.0 if args.no_extra_legs else args.sustain_s, dec_layers=args.dec_layers)
+                     0.0 if args.no_extra_legs else args.sustain_s, dec_layers=args.dec_layers, dump_dir=args.dump_outputs)
     extra, full = {}, {}
     default_shape = (Hh, T, args.enc_layers, B, args.dtype, args.cell, args.dec_layers) == (512, 25, 1, 2048, "f32", "gru", 1)
 

@@ -174,7 +174,13 @@ OVERLAP = _os.environ.get('CPG_NO_OVERLAP', '') == '' and not _os.environ.get('C
 
 
 def side_streams(device, n=3):
-    """Per-device pool of side HIP streams (created once)."""
+    """Per-device pool of side HIP streams (created once).  While the current stream is being captured into a hipGraph every
+    "side" stream is the capturing stream itself: a captured fork / join gives the graph parallel branches, and hipGraphLaunch
+    of this HIP runtime can segfault on the host while it assigns such branches to its pooled streams.  The branches' launches
+    (same kernels, same split-K options) then run in issue order on the one stream; their scratch is per-call, so sharing the
+    stream-keyed workspaces is safe."""
+    if torch.cuda.is_current_stream_capturing():
+        return [torch.cuda.current_stream()] * n
     key = device.index if device.index is not None else torch.cuda.current_device()
     if key not in _side:
         _side[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
