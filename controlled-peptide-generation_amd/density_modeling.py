@@ -2,7 +2,8 @@
 
 Counterpart of the reference's density_modeling.py: RejSampleBase :38-60 and mogQ :63-80 (the alternatives fullQ /
 gaussianQ / evaluate_nll are diagnostics outside the hot path and not provided).
-  * the proposal Q_xi(z) is a diagonal Gaussian mixture fitted ONCE on the host with scikit-learn, as in the reference;
+  * the proposal Q_xi(z) is a diagonal Gaussian mixture fitted ONCE on the host with scikit-learn, as in the reference, or on the
+    device with mogQ(..., fit='gpu') (cpg.gmm.DiagGaussianMixture: the same algorithm and draws, in HIP);
   * `rejection_sample(n)` keeps the reference's return triple (samples_z torch f32 [n,D], scores dict of float64 arrays,
     accepted bool array); the arithmetic - mixture draw, logistic-regression scoring of every attribute, product and the
     accept test - runs in two HIP kernels (cpg_gmm_sample, cpg_lr_score_accept);
@@ -100,14 +101,23 @@ class RejSampleBase:
 
 
 class mogQ(RejSampleBase):
-    def __init__(self, mu, logvar, n_components=10, z_num_samples=10, **mog_kwargs):
-        import sklearn.mixture
+    def __init__(self, mu, logvar, n_components=10, z_num_samples=10, fit='sklearn', **mog_kwargs):
+        """fit='sklearn' (default): the reference's host fit.  fit='gpu': the same z, fitted on the device by
+        cpg.gmm.DiagGaussianMixture (covariance_type='diag' only; same draws from numpy's global generator as scikit-learn)."""
+        if fit not in ('sklearn', 'gpu'):
+            raise ValueError("fit must be 'sklearn' or 'gpu', got %r" % (fit,))
         self.mu, self.logvar = mu, logvar
         self.N, self.D = mu.shape
         self.z = torch.cat([mu + (0.5 * logvar).exp() * torch.randn_like(logvar) for _ in range(z_num_samples)], dim=0)
         self.n_components = n_components
-        self.mog = sklearn.mixture.GaussianMixture(n_components=n_components, **mog_kwargs)
-        self.mog.fit(self.z.cpu().numpy())
+        if fit == 'gpu':
+            from cpg.gmm import DiagGaussianMixture
+            self.mog = DiagGaussianMixture(n_components=n_components, device=self.device, **mog_kwargs)
+            self.mog.fit(self.z)
+        else:
+            import sklearn.mixture
+            self.mog = sklearn.mixture.GaussianMixture(n_components=n_components, **mog_kwargs)
+            self.mog.fit(self.z.cpu().numpy())
         print('mog-{}. Converged: {} in {} iters, log likelihood lower bound: {:.4f}'.format(
             n_components, self.mog.converged_, self.mog.n_iter_, self.mog.lower_bound_))
         self._upload()

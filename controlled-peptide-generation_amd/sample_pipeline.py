@@ -33,7 +33,7 @@ LOG = logging.getLogger('GenerationAPI')
 logging.basicConfig(format='%(asctime)s %(message)s', datefmt='%m/%d/%Y %I:%M:%S %p', level=logging.INFO)
 
 Q_CLASS = mogQ
-Q_KWARGS = {'n_components': None, 'z_num_samples': 10, 'covariance_type': None}
+Q_KWARGS = {'n_components': None, 'z_num_samples': 10, 'covariance_type': None, 'fit': 'sklearn'}
 
 
 def decode_from_z(z, model, dataset, sample_mode='beam', beam_size=5, chunk=1024, c=None):
@@ -610,6 +610,7 @@ def build_parser():
     parser.add_argument('--QClass', default='mogQ')
     parser.add_argument('--Q_n_components', type=int, default=100)
     parser.add_argument('--Q_covariance_type', default='diag')
+    parser.add_argument('--Q_fit', choices=['sklearn', 'gpu'], default='sklearn')
     parser.add_argument('--Q_select_amppos', type=int, default=0)
     parser.add_argument('--Q_from_full_dataloader', type=int, default=0)
     parser.add_argument('--n_samples_per_round', type=int, default=5000)

@@ -579,6 +579,43 @@ CPG_API int cpg_lr_score_accept(const float* z, int n, int D, const double* coef
                                 const int32_t* target, int A, const double* uniforms, double* probs, double* accum,
                                 uint8_t* accepted, void* stream);
 
+/* ---- Fitting the CLaSS proposal Q(z) (density_modeling.py mogQ: sklearn GaussianMixture(covariance_type='diag').fit), in the
+ * element type of X: dbytes = 4 (float) or 8 (double), 1 <= D, K <= 128.  Cross-workgroup sums are f64, reduced in a fixed order.
+ * Parameter block (cpg_gmm_params_elems elements of that type): w[K] logw[K] logdet[K] smp[K] means[K,D] covars[K,D]
+ * pchol[K,D] (precisions_cholesky_) mp[K,D] prec[K,D].  Workspaces: cpg_gmm_workspace / cpg_kmeans_pp_workspace
+ * bytes (no device needed). */
+CPG_API size_t cpg_gmm_workspace(size_t n, int D, int K);
+CPG_API size_t cpg_gmm_params_elems(int D, int K);
+/* column sums of (X - shift) and of its square -> out f64 [2, D] (shift f64 [D] or null): X.mean(0), np.var(X, 0) for KMeans' tol */
+CPG_API int cpg_gmm_colstats(const void* X, size_t n, int D, int dbytes, const double* shift, double* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* sklearn.cluster._kmeans._kmeans_plusplus (n_local_trials = n_trials <= 16) on X - mean (mean [D] or null: X as it is).  first =
+ * random_state.choice(n, p=w/w.sum()); uniforms f64 [K-1, n_trials] = the random_state.uniform(size=n_trials) of each further
+ * center; the host draws both, in that order.  -> indices int64 [K], centers [K, D] (rows of X - mean), labels[indices[c]] = c
+ * when labels is not null (GaussianMixture init_params='k-means++').  Every step stays on the device: no synchronisation. */
+CPG_API size_t cpg_kmeans_pp_workspace(size_t n, int n_trials);
+CPG_API int cpg_kmeans_pp(const void* X, size_t n, int D, int dbytes, const void* mean, int64_t first, const double* uniforms,
+                          int K, int n_trials, int64_t* indices, void* centers, int32_t* labels, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* One iteration of sklearn.cluster._k_means_lloyd.lloyd_iter_chunked_dense on X - mean: labels (argmin, lowest index on ties;
+ * in: the previous labels, -1 before the first), and with update = 1 the new centers (empty clusters relocated as
+ * _relocate_empty_clusters_dense does), rowdist [n] (distance of each row to its old center), status f64 [2] = (labels changed,
+ * center_shift_tot).  update = 0: labels only (the final E-step of _kmeans_single_lloyd). */
+CPG_API int cpg_kmeans_lloyd_step(const void* X, size_t n, int D, int K, int dbytes, const void* mean, const void* centers,
+                                  void* centers_new, int32_t* labels, void* rowdist, double* status, int update, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* the derived entries (logw, logdet, smp = sum means^2 prec, mp = means * prec, prec) of a block from w, means, pchol */
+CPG_API int cpg_gmm_params_prepare(void* params, int D, int K, int dbytes, void* stream);
+/* One GaussianMixture EM iteration (_e_step with params, then _m_step) in one pass over X: params_out = the new parameter block,
+ * *lower_bound = mean log_prob_norm of that E-step.  With labels int32 [n] instead of params (exactly one of the two): the
+ * one-hot responsibilities of _initialize (label -1 = no component), weights = nk / n. */
+CPG_API int cpg_gmm_em_step(const void* X, size_t n, int D, int K, int dbytes, const void* params, const int32_t* labels,
+                            double reg_covar, void* params_out, double* lower_bound, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* GaussianMixture.score_samples (log_prob_norm [n]), predict_proba (resp [n, K]) and predict (label [n]); any may be null */
+CPG_API int cpg_gmm_score(const void* X, size_t n, int D, int K, int dbytes, const void* params, void* log_prob_norm, void* resp,
+                          int32_t* label, void* stream);
+
 /* Residue rows of decoded ids: what dataset.idx2sentences(..., print_special_tokens=False) keeps of each row
  * (data_processing/dataset.py:285-300, called from sample_pipeline.py:129-139), as arrays.  ids int16 [n, L] (ids below
  * first_residue - the 4 specials, or -1 padding - are dropped); letters uint8 [n, L] left-aligned, zero-filled; counts [n]. */
